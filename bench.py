@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - throughput of the batched FFT filter hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 Workload (BASELINE.json configs[1]): CreateLowCutFilter(800) @ 44.1 kHz on 4096 mono channels x
 4096-sample chunks per GPU, float32, synthetic uniform(-1,1) input already resident in HBM.
@@ -19,7 +19,9 @@ also measured after the timed region and reported under "stream" ("one_stream": 
 per-kernel time and hipGraph replay; "resident": resident launches).  History is carried by the engine exactly as between
 reference apply() calls; every output sample of every step is produced inside the timed region.  Before the W warm-up steps the
 same workload runs untimed for --prewarm-ms (default 300 ms): an idle MI355X needs tens of milliseconds of sustained load before
-its shader clock has ramped up.
+its shader clock has ramped up.  In batch mode the engine's history is then reset and the W + runs x K counted launches read the
+resident batches in a fixed order, so with the same arguments the last timed launch computes the same output in every run;
+`--dump-outputs DIR` writes a fixed sample of it (DIR/output.npy) for comparing two builds.
 
 For N > 1 every rank owns its own channel shard (weak scaling); the only collective is the RCCL broadcast of the filter spectrum
 before the timed region.  The driver launches one rank per GPU with torch.distributed.run; plain `python bench.py --gpus N` does
@@ -90,6 +92,10 @@ def parse(argv=None):
                     "the line then says parity_checked false)")
     ap.add_argument("--explain", action="store_true", help="after the (compact) JSON line, list on stderr every explanatory string the line leaves out "
                                                            "(what each figure is, which entry points it timed); the same texts are in DESIGN.md section 6")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="batch mode: after the timed regions write what the LAST timed launch returned as DIR/output.npy (float32 "
+                         "[chunks, channels, chunk]: every chunk of the channels the parity check samples, at most 64 MB). With the same "
+                         "arguments the launch reads the same input, so two builds can be compared output for output")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-stream-extra", action="store_true")
     ap.add_argument("--no-latency", action="store_true")
@@ -109,6 +115,10 @@ def parse(argv=None):
     a = ap.parse_args(argv)
     if a.mode == "offline":
         a.mode = "batch"
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and a.mode != "batch":
+        ap.error("--dump-outputs needs --mode batch (the timed output of a step is an output batch there)")
     if os.environ.get("ADSP_BENCH_SMALL") == "1":
         # test hook (tests/test_gpu_round3.py: two ranks on one GPU): a sixteenth of the channels, short batches.  The line
         # says so ("small": true); never set by the driver
@@ -366,6 +376,11 @@ class Runner:
         while (time.perf_counter() - t_pre) * 1e3 < prewarm_ms:  # clock ramp: untimed, same workload
             run(unit)
             cuda_sync()
+        if self.mode != "stream":
+            # the clock ramp ran for a wall-clock time, i.e. a varying number of launches: the counted launches start from a fresh
+            # history at batch 0, so that with the same arguments the last timed launch reads the same data in every run (--dump-outputs)
+            eng.reset()
+            self.step_count = 0
         if warm:
             run(warm)
         cuda_sync()
@@ -420,6 +435,39 @@ class Runner:
         wall, kern_ms, launches, _ = runs[med]
         return steps, warm, wall, kern_ms, launches
 
+    def sampled_channels(self, n_channels=32):
+        """The channels the checks and --dump-outputs sample: the first and last eight (first and last workgroups, every XCD residue)
+        and n_channels - 16 spread over the rest by a generator seeded with the channel count - the same in every run."""
+        C = self.C
+        k = min(n_channels, C)
+        rng = np.random.default_rng(C)
+        mid = sorted(int(c) for c in rng.choice(np.arange(8, max(9, C - 8)), max(0, k - 16), replace=False)) if C > 16 + (k - 16) else []
+        return sorted(set(list(range(min(8, C))) + mid + list(range(max(0, C - 8), C))))
+
+    def dump_outputs(self, out_dir, max_bytes=64_000_000):
+        """--dump-outputs: the output batch of the LAST timed launch, as adsp_apply_device hands it to its caller, for the sampled
+        channels -> out_dir/output.npy, float32 [chunks, channels, chunk] (int16 batches converted exactly).  Where those channels
+        exceed max_bytes, a subset of the chunks drawn by a generator seeded with the batch length is kept (in order)."""
+        torch = self.torch
+        j = self.step_count - 1
+        y = self.outs[j % 2]
+        chans = self.sampled_channels()
+        per_chunk = len(chans) * self.N * 4
+        if per_chunk > max_bytes:
+            raise SystemExit(f"bench.py: --dump-outputs: one chunk of {len(chans)} channels is {per_chunk} bytes, more than {max_bytes}")
+        rows = np.arange(self.cps)
+        if rows.size * per_chunk > max_bytes:
+            rows = np.sort(np.random.default_rng(self.cps).choice(rows, max_bytes // per_chunk, replace=False))
+        with torch.cuda.device(y.device):
+            sel = y.index_select(1, torch.tensor(chans, device=y.device))
+            if rows.size != self.cps:
+                sel = sel.index_select(0, torch.tensor(rows, device=y.device))
+            out = sel.float().cpu().numpy()
+        os.makedirs(out_dir, exist_ok=True)
+        path = os.path.join(out_dir, "output.npy")
+        np.save(path, out)
+        return path, out.shape, j
+
     def parity_check(self, fir, n_channels=32):
         """What the timed region produced, checked: the output batch of the LAST timed launch, for `n_channels` channels (the
         first and last eight - first and last workgroups, every XCD residue - and sixteen spread over the rest), every
@@ -432,10 +480,7 @@ class Runner:
         j = self.step_count - 1
         x, prev, y = self.ins[j % self.n_in], self.ins[(j - 1) % self.n_in], self.outs[j % 2]
         C, N, cps = self.C, self.N, self.cps
-        k = min(n_channels, C)
-        rng = np.random.default_rng(C)
-        mid = sorted(int(c) for c in rng.choice(np.arange(8, max(9, C - 8)), max(0, k - 16), replace=False)) if C > 16 + (k - 16) else []
-        chans = sorted(set(list(range(min(8, C))) + mid + list(range(max(0, C - 8), C))))
+        chans = self.sampled_channels(n_channels)
         idx = torch.tensor(chans, device=x.device)
         hist = self.eng.geometry.history_chunks
         xin = torch.cat([prev[cps - hist:].index_select(1, idx), x.index_select(1, idx)], 0).contiguous()
@@ -1069,7 +1114,10 @@ def main():
         return r, runs, pblock
 
     main_run, runs, parity = measure_everywhere(args, args.mode, fir, args.steps, args.warmup, args.prewarm_ms, args.runs, True)
-    steps, warm = max(1, args.steps), args.warmup
+    steps, warm = args.steps, args.warmup
+    if args.dump_outputs and rank == 0:  # (before the parity verdict and before the figures below free the batches)
+        path, shape, launch = main_run.dump_outputs(args.dump_outputs)
+        sys.stderr.write(f"bench.py: wrote {path}: float32 {list(shape)} of the output of counted launch {launch} (rank 0)\n")
     if args.single_process:
         world = ndev  # whole-job aggregate below
     dist_info = {}

@@ -62,3 +62,22 @@ def test_other_workloads_and_the_rccl_path_print_the_same_line():
     # ... and the same collective once more through the C ABI (adsp_bcast_spectrum_rank), cross-checked against the torch carrier
     chk = d["abi_carrier_check"]
     assert chk["ranks_ok"] == 1 and chk["equal_on_all_ranks"] and chk["matches_torch_carrier"], chk
+
+
+def test_dump_outputs_is_the_same_in_every_run_and_follows_steps(tmp_path):
+    """--dump-outputs: the last timed launch's output for the sampled channels, float32 [chunks, channels, chunk] under 64 MB.  The clock
+    ramp runs for a wall-clock time (a varying number of launches); the counted launches after it do not depend on it, so two runs with
+    the same arguments dump the same bits, and another --steps is another launch over another input batch."""
+    import numpy as np
+    common = ("--warmup", "1", "--no-stream-extra", "--no-latency", "--no-cpu-baseline", "--no-configs")
+    outs = {}
+    for tag, steps, prewarm in (("a", "3", "5"), ("b", "3", "60"), ("c", "4", "5")):
+        d, _ = run_bench("--steps", steps, *common, "--prewarm-ms", prewarm, "--dump-outputs", str(tmp_path / tag))
+        assert d["steps"] == int(steps) and d["roofline"]["launches"] == int(steps) and d["parity_checked"] is True
+        outs[tag], cps = np.load(tmp_path / tag / "output.npy"), d["config"]["chunks_per_step"]
+        assert sorted(os.listdir(tmp_path / tag)) == ["output.npy"]
+    a = outs["a"]
+    assert a.dtype == np.float32 and a.shape == (cps, 32, 4096) and a.nbytes <= 64_000_000
+    assert np.isfinite(a).all() and np.abs(a).max() > 0.05
+    assert np.array_equal(a, outs["b"]), "same arguments, different outputs"
+    assert not np.array_equal(a, outs["c"]), "--steps 4 dumped the same launch as --steps 3"

@@ -1,6 +1,6 @@
 #!/bin/bash
 # run ON the GPU box: bench (batch) under a GRBM_GUI_ACTIVE pmc pass, print kernel time and effective clock
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 cd /tmp && export TMPDIR=/tmp
 TAG=$1; shift
 rm -rf /tmp/clk_$TAG

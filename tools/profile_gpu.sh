@@ -3,7 +3,7 @@
 # usage: tools/profile_gpu.sh <tag> [bench args...]
 set -u
 TAG=$1; shift
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
